@@ -8,7 +8,13 @@ synthetic data, random-init weights. N>1 runs one rank per GPU over RCCL
 (launched by torch.distributed.run); global batch stays 256 (strong scaling,
 BASELINE config 3).
 
+A plain run sets up, warms up, times --steps train steps and prints one JSON
+result line. --dump-outputs DIR also writes what the last timed step computed
+(see _dump_outputs). --full is reserved for measurements beyond the headline
+figure; there are none today, so it changes nothing.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+                       [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -16,6 +22,39 @@ import os
 import time
 
 import torch
+
+# cap per dumped state vector: 2 vectors x 2M x 4 B = 16 MB, well under 64 MB
+_DUMP_SAMPLE = 2 * 1024 * 1024
+
+
+def _dump_outputs(out_dir, trainer, loss, rank):
+    """Write the results of the last timed train step as <name>.npy.
+
+    A caller of train_step receives the loss and the updated trainer state:
+    the fp32 master parameters and their EMA. Vectors longer than
+    _DUMP_SAMPLE are reduced to a fixed, seeded sample of their elements,
+    the same indices in every run."""
+    import numpy as np
+
+    opt = trainer.optimizer
+    total = opt.flat.numel()
+    idx = None
+    if total > _DUMP_SAMPLE:
+        picks = np.random.RandomState(2024).choice(total, _DUMP_SAMPLE,
+                                                   replace=False)
+        idx = torch.from_numpy(np.sort(picks)).to(opt.flat.device)
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    os.makedirs(out_dir, exist_ok=True)
+
+    def save(name, arr):
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
+
+    save("loss", np.asarray([loss], dtype=np.float64))
+    for name, vec in (("params", opt.flat), ("ema_params", opt.ema)):
+        vec = vec.detach()
+        if idx is not None:
+            vec = vec[idx]
+        save(name, vec.to("cpu", torch.float32).numpy())
 
 
 def main():
@@ -28,7 +67,15 @@ def main():
     ap.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--profile", action="store_true",
                     help="per-step hipEvent timings to stderr (SURVEY §5.1)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's loss, "
+                         "parameters and EMA as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline "
+                         "figure (none today)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -125,6 +172,9 @@ def main():
         el_dev = el.to(dev) if use_gpu else el
         dist.all_reduce(el_dev, op=dist.ReduceOp.MAX)
         elapsed = float(el_dev.item())
+
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, trainer, loss, rank)
 
     images_total = args.global_batch if world > 1 else local_batch
     value = images_total * args.steps / elapsed
