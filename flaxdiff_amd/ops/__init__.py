@@ -16,6 +16,7 @@ Hot-op inventory (SURVEY.md §2.10 native-code inventory):
 from __future__ import annotations
 
 import os
+import weakref
 from typing import Optional
 
 import torch
@@ -64,6 +65,69 @@ def _use_hip(x: torch.Tensor) -> bool:
 
 
 # ---------------------------------------------------------------------------
+# Gradient sinks: parameter gradients accumulate in place
+# ---------------------------------------------------------------------------
+# FlatAdamWEMA (trainer/optim.py) points every p.grad at a slice of one fp32
+# flat buffer and attaches the same slice as `p._grad_sink`. The backward
+# kernels that produce a parameter gradient (wgrad reduce, colsum, GN/RMSNorm
+# dgamma/dbeta) ADD their result straight into that slice and the autograd
+# Function returns None for it: no zero-filled temporary per gradient and no
+# AccumulateGrad add kernel behind it.
+
+_GRAD_HOOK_OWNERS: "weakref.WeakSet" = weakref.WeakSet()
+
+
+def register_grad_hook_owner(owner) -> None:
+    """Register an object whose per-parameter post-accumulate-grad hooks must
+    see every gradient arrive (parallel.GradBucketSynchronizer). It exposes
+    `hooks_live`; while any owner's hooks are live, sinks are off — a
+    Function that returns None never fires those hooks."""
+    _GRAD_HOOK_OWNERS.add(owner)
+
+
+def _sink_kinds() -> str:
+    """Gradient kinds that take sinks: w (conv/dense weights), b (biases),
+    g (GroupNorm gamma/beta), r (RMSNorm gamma). FD_GRAD_SINK=0 turns all
+    off, =all turns all on. The default leaves the weight gradients on the
+    returned route: with them the flagship step's loss after 25 steps moved
+    by 3e-3, outside the run-to-run spread of the returned route (2e-5),
+    although every per-parameter gradient matched it to run-to-run noise
+    (profiles/grad_sink_ab.md) — unexplained, so not the default."""
+    v = os.environ.get("FD_GRAD_SINK", "1")
+    if v == "0":
+        return ""
+    return "wbgr" if v == "all" else "bgr"
+
+
+def grad_sinks_active() -> bool:
+    """THE sink predicate, evaluated when backward runs. Off under
+    FD_GRAD_SINK=0 and whenever live (enabled, not suspended) bucket hooks
+    count gradient arrivals — i.e. on only in a single process and inside the
+    captured region of the distributed graph step."""
+    if not _sink_kinds():
+        return False
+    return not any(o.hooks_live for o in _GRAD_HOOK_OWNERS)
+
+
+def _grad_sink(p: Optional[torch.Tensor], kind: str) -> Optional[torch.Tensor]:
+    """fp32 buffer the kernels may accumulate p's gradient into, or None for
+    the returned-gradient route. The sink must still BE the owning
+    parameter's .grad (someone may have reset it since the optimizer wired
+    it); a reshaped view of a parameter names its owner in _grad_sink_owner."""
+    if p is None or kind not in _sink_kinds():
+        return None
+    sink = getattr(p, "_grad_sink", None)
+    if sink is None or sink.dtype != torch.float32 or not grad_sinks_active():
+        return None
+    owner = getattr(p, "_grad_sink_owner", None)
+    g = (p if owner is None else owner).grad
+    if g is None or g.data_ptr() != sink.data_ptr() \
+            or g.numel() != sink.numel() or not sink.is_contiguous():
+        return None
+    return sink
+
+
+# ---------------------------------------------------------------------------
 # GroupNorm (+ optional fused SiLU)
 # ---------------------------------------------------------------------------
 
@@ -77,6 +141,7 @@ class _GroupNormSiLUFn(torch.autograd.Function):
         ctx.silu = silu
         ctx.has_beta = beta is not None
         ctx.beta = beta
+        ctx.gamma_param = gamma
         return y
 
     @staticmethod
@@ -84,6 +149,12 @@ class _GroupNormSiLUFn(torch.autograd.Function):
         x, gamma, mean, rstd = ctx.saved_tensors
         ext = _require_ext()
         beta = ctx.beta if ctx.has_beta else torch.zeros_like(gamma)
+        if ctx.has_beta and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+            sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
+            if sg is not None and sb is not None:
+                (dx,) = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta, mean,
+                                        rstd, ctx.groups, ctx.silu, sg, sb)
+                return dx, None, None, None, None, None
         dx, dgamma, dbeta = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta,
                                             mean, rstd, ctx.groups, ctx.silu)
         return dx, dgamma, (dbeta if ctx.has_beta else None), None, None, None
@@ -106,12 +177,17 @@ class _RMSNormFn(torch.autograd.Function):
         ext = _require_ext()
         y, rrms = ext.rms_norm_fwd(x, gamma, eps)
         ctx.save_for_backward(x, gamma, rrms)
+        ctx.gamma_param = gamma
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, rrms = ctx.saved_tensors
         ext = _require_ext()
+        sink = _grad_sink(ctx.gamma_param, "r") if ctx.needs_input_grad[1] else None
+        if sink is not None:
+            (dx,) = ext.rms_norm_bwd(dy.contiguous(), x, gamma, rrms, sink)
+            return dx, None, None
         dx, dgamma = ext.rms_norm_bwd(dy.contiguous(), x, gamma, rrms)
         return dx, dgamma, None
 
@@ -214,6 +290,7 @@ class _Conv2dFn(torch.autograd.Function):
         ctx.has_badd = badd is not None
         ctx.w_dtype = w.dtype
         ctx.b_dtype = b.dtype if b is not None else None
+        ctx.w_param, ctx.b_param = w, b
         return y
 
     @staticmethod
@@ -224,14 +301,13 @@ class _Conv2dFn(torch.autograd.Function):
         dx = ext.conv2d_dgrad(dy, wk, ctx.stride, x.shape[1], x.shape[2]) \
             if ctx.needs_input_grad[0] else None
         dw = db = None
+        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
+            else None
         if ctx.needs_input_grad[1]:
-            dw, _db_unused = ext.conv2d_wgrad(dy, x, wk.shape[0], wk.shape[1],
-                                              ctx.stride)
-            dw = dw if ctx.w_dtype == torch.float32 else dw.to(ctx.w_dtype)
-        if ctx.has_bias:
-            db = _bias_grad(dy)          # fp32
-            if ctx.b_dtype != torch.float32:
-                db = db.to(ctx.b_dtype)
+            dw, db = _wgrad(ext, dy, x, wk.shape[0], wk.shape[1], ctx.stride,
+                            ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
+        elif ctx.has_bias:
+            db = _bias_grad(dy, b_param, ctx.b_dtype)
         dadd = dy if ctx.has_add else None   # y = conv + add -> d(add) = dy
         dbadd = None
         if ctx.has_badd:                     # d(badd)[b,c] = sum_hw dy
@@ -271,6 +347,7 @@ class _DenseFn(torch.autograd.Function):
         ctx.has_add = add is not None
         ctx.w_dtype = w2d.dtype
         ctx.b_dtype = b.dtype if b is not None else None
+        ctx.w_param, ctx.b_param = w2d, b
         return y
 
     @staticmethod
@@ -285,19 +362,18 @@ class _DenseFn(torch.autograd.Function):
                 dx = torch.matmul(dy, wk.t())
         else:
             dx = None
-        dw = None
+        dw = db = None
+        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
+            else None
         if ctx.needs_input_grad[1]:
             M = x2d.shape[0]
-            dw4, _ = ext.conv2d_wgrad(dy.view(M, 1, 1, dy.shape[1]),
-                                      x2d.view(M, 1, 1, x2d.shape[1]), 1, 1, 1)
-            dw = dw4.view(x2d.shape[1], dy.shape[1])
-            if ctx.w_dtype != torch.float32:
-                dw = dw.to(ctx.w_dtype)
-        db = None
-        if ctx.has_bias:
-            db = _bias_grad(dy)
-            if ctx.b_dtype != torch.float32:
-                db = db.to(ctx.b_dtype)
+            dw, db = _wgrad(ext, dy.view(M, 1, 1, dy.shape[1]),
+                            x2d.view(M, 1, 1, x2d.shape[1]), 1, 1, 1,
+                            ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
+            if dw is not None:
+                dw = dw.view(x2d.shape[1], dy.shape[1])
+        elif ctx.has_bias:
+            db = _bias_grad(dy, b_param, ctx.b_dtype)
         dadd = dy if ctx.has_add else None   # y = xW + add -> d(add) = dy
         return dx, dw, db, dadd
 
@@ -377,6 +453,7 @@ class _ConvUp2xFn(torch.autograd.Function):
         ctx.has_bias = b is not None
         ctx.w_dtype = w.dtype
         ctx.b_dtype = b.dtype if b is not None else None
+        ctx.w_param, ctx.b_param = w, b
         return y
 
     @staticmethod
@@ -386,17 +463,17 @@ class _ConvUp2xFn(torch.autograd.Function):
         dy = dy.contiguous()
         H2, W2 = x.shape[1] * 2, x.shape[2] * 2
         dx = db = dw = None
+        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
+            else None
         if ctx.needs_input_grad[0]:
             dx_up = ext.conv2d_dgrad(dy, wk, 1, H2, W2)
             dx = ext.upsample2x_bwd(dx_up)
         if ctx.needs_input_grad[1]:
             x_up = ext.upsample2x_fwd(x)
-            dw, _ = ext.conv2d_wgrad(dy, x_up, 3, 3, 1)
-            dw = dw if ctx.w_dtype == torch.float32 else dw.to(ctx.w_dtype)
-        if ctx.has_bias:
-            db = _bias_grad(dy)
-            if ctx.b_dtype != torch.float32:
-                db = db.to(ctx.b_dtype)
+            dw, db = _wgrad(ext, dy, x_up, 3, 3, 1, ctx.w_param, ctx.w_dtype,
+                            b_param, ctx.b_dtype)
+        elif ctx.has_bias:
+            db = _bias_grad(dy, b_param, ctx.b_dtype)
         return dx, dw, db
 
 
@@ -466,13 +543,43 @@ def cat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.cat([a, b], dim=-1)
 
 
-def _bias_grad(dy: torch.Tensor) -> torch.Tensor:
-    """Column sum over all but the channel dim (coalesced HIP kernel)."""
+def _wgrad(ext, dy, x, kh, kw, stride, w_param, w_dtype,
+           b_param=None, b_dtype=None):
+    """(dw, db) through the split-M kernels; `b_dtype` set asks for the bias
+    gradient too. With a live gradient sink on a parameter the reduce adds
+    into it and None comes back for that gradient (autograd then has nothing
+    left to accumulate); otherwise the fp32 result is returned, cast to the
+    parameter's dtype. The tr16 kernel families fold the bias gradient into
+    the wgrad kernel; the other routes column-sum dy (_bias_grad)."""
+    want_db = b_dtype is not None
+    w_sink = _grad_sink(w_param, "w") if w_dtype == torch.float32 else None
+    b_sink = _grad_sink(b_param, "b") if b_dtype == torch.float32 else None
+    dw, db, folded = ext.conv2d_wgrad(dy, x, kh, kw, stride, w_sink,
+                                      want_db, b_sink)
+    if dw is not None and w_dtype != torch.float32:
+        dw = dw.to(w_dtype)
+    if want_db and not folded:
+        db = _bias_grad(dy, b_param, b_dtype)
+    elif db is not None and b_dtype != torch.float32:
+        db = db.to(b_dtype)
+    return dw, db
+
+
+def _bias_grad(dy: torch.Tensor, b_param: Optional[torch.Tensor] = None,
+               b_dtype=torch.float32) -> Optional[torch.Tensor]:
+    """Column sum over all but the channel dim (coalesced HIP kernel). With
+    a live gradient sink on `b_param` the kernel's atomics add into it and
+    None is returned."""
     d2 = dy.reshape(-1, dy.shape[-1])
     C = d2.shape[1]
     if d2.is_cuda and d2.dtype == torch.bfloat16 and C % 8 == 0 and C <= 2048:
-        return _require_ext().colsum(d2.contiguous())
-    return d2.float().sum(0)
+        sink = _grad_sink(b_param, "b") if b_dtype == torch.float32 else None
+        db = _require_ext().colsum(d2.contiguous(), sink)
+        if sink is not None:
+            return None
+    else:
+        db = d2.float().sum(0)
+    return db if b_dtype == torch.float32 else db.to(b_dtype)
 
 
 def conv2d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
@@ -497,6 +604,12 @@ def conv2d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor] = None,
             sht = getattr(w, "_shadow_bf16_t", None)
             if sht is not None:
                 w2._shadow_bf16_t = sht
+            sink = getattr(w, "_grad_sink", None)
+            if sink is not None:
+                # same storage, reshaped; the predicate checks it against
+                # the owning parameter's .grad when backward runs
+                w2._grad_sink = sink.reshape(w.shape[2], w.shape[3])
+                w2._grad_sink_owner = w
         y = dense(x.reshape(-1, w.shape[2]), w2, b)
         y = y.reshape(*x.shape[:-1], w.shape[3])
         if badd is not None:
@@ -562,9 +675,8 @@ class _ConvTransposeFn(torch.autograd.Function):
             if ctx.needs_input_grad[0] else None
         dwf = None
         if ctx.needs_input_grad[1]:
-            dwf, _ = ext.conv2d_wgrad(x, dout, wf.shape[0], wf.shape[1],
-                                      ctx.stride)
-            dwf = dwf.to(wf.dtype)
+            dwf = ext.conv2d_wgrad(x, dout, wf.shape[0], wf.shape[1],
+                                   ctx.stride)[0].to(wf.dtype)
         return dx, dwf, None
 
 

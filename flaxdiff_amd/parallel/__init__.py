@@ -157,6 +157,16 @@ class GradBucketSynchronizer:
         if self.enabled:
             for off, n, p in ranges:
                 p.register_post_accumulate_grad_hook(self._hook)
+        # the hooks only fire for gradients autograd itself accumulates, so
+        # in-place gradient sinks (ops.grad_sinks_active) stay off while the
+        # hooks are live
+        from .. import ops
+        ops.register_grad_hook_owner(self)
+
+    @property
+    def hooks_live(self) -> bool:
+        """True while the per-parameter hooks count gradient arrivals."""
+        return self.enabled and not self.suspended
 
     def _hook(self, p):
         if self.suspended:

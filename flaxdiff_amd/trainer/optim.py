@@ -66,6 +66,11 @@ class FlatAdamWEMA:
                 p.data = self.flat[off:off + n].view(p.shape)
                 p.grad = self.flat_grad[off:off + n].view(p.shape)
                 p._shadow_bf16 = self.flat_bf16[off:off + n].view(p.shape)
+                # gradient sink: the native backward kernels add this
+                # parameter's gradient straight into its flat_grad slice
+                # (ops._grad_sink), skipping the per-gradient temporary and
+                # autograd's accumulate kernel
+                p._grad_sink = p.grad
                 self.offsets.append(off)
                 off += n
         self.ema.copy_(self.flat)
