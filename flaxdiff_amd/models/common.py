@@ -124,6 +124,15 @@ class GroupNorm(nn.Module):
         return ops.group_norm(x, self.num_groups, _cast(self.weight, x.dtype),
                               _cast(self.bias, x.dtype), self.eps, silu)
 
+    def forward_fork(self, x: torch.Tensor, silu: bool = False):
+        """-> (norm(x), x_pass) for an x with a second consumer: feeding that
+        consumer from x_pass lets the backward kernel sum its gradient into
+        dx (ops.group_norm_fork). Off the HIP path x_pass is x."""
+        if x.is_cuda:
+            return ops.group_norm_fork(x, self.num_groups, self.weight,
+                                       self.bias, self.eps, silu)
+        return self.forward(x, silu), x
+
 
 class RMSNorm(nn.Module):
     def __init__(self, dim: int, eps: float = 1e-5):
@@ -367,8 +376,15 @@ class ResidualBlock(nn.Module):
 
     def forward(self, x: torch.Tensor, temb: torch.Tensor,
                 textemb: torch.Tensor = None, extra_features: torch.Tensor = None):
-        residual = x
-        out = self._norm_act(self.norm1, x)
+        if isinstance(self.norm1, GroupNorm):
+            # x feeds norm1 and the residual branch: the fork hands both
+            # gradients to the GroupNorm backward kernel
+            out, residual = self.norm1.forward_fork(x, silu=self._fused_silu)
+            if not self._fused_silu:
+                out = self.activation(out)
+        else:
+            residual = x
+            out = self._norm_act(self.norm1, x)
         t = self.temb_projection(temb.to(out.dtype))
         if isinstance(self.conv1, Conv):
             # temb broadcast fused into the conv epilogue (one fewer full

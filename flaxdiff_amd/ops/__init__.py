@@ -167,6 +167,66 @@ def group_norm(x: torch.Tensor, groups: int, gamma: torch.Tensor,
     return reference.group_norm_nhwc(x, groups, gamma, beta, eps, silu)
 
 
+class _GroupNormForkFn(torch.autograd.Function):
+    """GroupNorm(+SiLU) of an x that has a second consumer. Returns (y, x):
+    the caller feeds the second consumer from the returned x, so autograd
+    hands both gradients to ONE backward and gn_silu_bwd folds the second
+    into dx (fp32 sum, one rounding) instead of a bf16 add pass behind it."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, groups, eps, silu):
+        ext = _require_ext()
+        # an output nobody consumed must arrive as None in backward, not as a
+        # zero-filled tensor: an unused x_pass then costs nothing
+        ctx.set_materialize_grads(False)
+        y, mean, rstd = ext.gn_silu_fwd(x, gamma, beta, groups, eps, silu)
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.groups = groups
+        ctx.silu = silu
+        ctx.beta = beta
+        ctx.gamma_param = gamma
+        return y, x                         # autograd re-wraps x as its own view
+
+    @staticmethod
+    def backward(ctx, dy, dx_pass):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        ext = _require_ext()
+        if dy is None:                      # only the pass-through was used
+            return dx_pass, None, None, None, None, None
+        add = None
+        if dx_pass is not None:
+            # a fresh dx is written; dx_pass is only read (it is usually a dy
+            # that conv2's dgrad/wgrad read as well)
+            add = dx_pass.to(x.dtype).contiguous()
+        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+            sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
+            if sg is not None and sb is not None:
+                (dx,) = ext.gn_silu_bwd(dy.contiguous(), x, gamma, ctx.beta,
+                                        mean, rstd, ctx.groups, ctx.silu,
+                                        sg, sb, add)
+                return dx, None, None, None, None, None
+        dx, dgamma, dbeta = ext.gn_silu_bwd(dy.contiguous(), x, gamma, ctx.beta,
+                                            mean, rstd, ctx.groups, ctx.silu,
+                                            None, None, add)
+        return dx, dgamma, dbeta, None, None, None
+
+
+def group_norm_fork_enabled() -> bool:
+    """FD_GN_FORK_ADD=0 keeps the two gradients of a forked x on autograd's
+    own add."""
+    return os.environ.get("FD_GN_FORK_ADD", "1") != "0"
+
+
+def group_norm_fork(x: torch.Tensor, groups: int, gamma: torch.Tensor,
+                    beta: torch.Tensor, eps: float = 1e-5, silu: bool = False):
+    """-> (group_norm(x), x_pass). Use x_pass wherever else x is consumed;
+    on the HIP path its gradient is then summed inside the GroupNorm
+    backward kernel."""
+    if _use_hip(x) and beta is not None and group_norm_fork_enabled():
+        return _GroupNormForkFn.apply(x.contiguous(), gamma, beta, groups, eps, silu)
+    return group_norm(x, groups, gamma, beta, eps, silu), x
+
+
 # ---------------------------------------------------------------------------
 # RMSNorm (last-dim)
 # ---------------------------------------------------------------------------
@@ -735,6 +795,38 @@ def depthwise_conv2d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
 # recomputes P from saved LSE and runs the 5 grads as MFMA GEMMs.
 # ---------------------------------------------------------------------------
 
+def _attn_view_ok(t: torch.Tensor) -> bool:
+    """What the attention kernels address in place (att_layout_ok in
+    hip/common.h): any dense tensor, as ever, or a [B,H,S,D] view with a dense
+    last dim, the other strides positive multiples of 8 elements and a
+    16-byte-aligned base."""
+    if t.dim() != 4:
+        return False
+    if t.is_contiguous():
+        return True
+    if t.stride(3) != 1 or t.data_ptr() % 16 or t.stride(2) >= 2 ** 31:
+        return False
+    return all(st > 0 and st % 8 == 0 for st in t.stride()[:3])
+
+
+def _attn_strided(q: torch.Tensor, k: torch.Tensor) -> bool:
+    """Strided route: q/k/v/do go to the kernels as the views they are and
+    o/dq/dk/dv come back in the layouts of q/q/k/v, so the model's
+    reshape+permute on either side of attention costs no copy kernel. Only
+    where the backward is the v2 small-KV kernel; the v1 route and the
+    composed backward keep their contiguous copies. FD_ATTN_STRIDED=0
+    restores the copies everywhere."""
+    if os.environ.get("FD_ATTN_STRIDED", "1") == "0":
+        return False
+    if os.environ.get("FD_ATTN_BWD_V1"):
+        return False
+    return k.shape[2] <= 128 and q.shape[3] <= 64
+
+
+def _attn_operand(t: torch.Tensor, strided: bool) -> torch.Tensor:
+    return t if strided and _attn_view_ok(t) else t.contiguous()
+
+
 class _AttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale):
@@ -756,7 +848,8 @@ class _AttentionFn(torch.autograd.Function):
         if k.shape[2] <= 128 and q.shape[3] <= dmax:
             ext = _require_ext()
             fn = ext.attn_bwd_smallkv if use_v1 else ext.attn_bwd_smallkv_v2
-            dq, dk, dv = fn(q, k, v, do.contiguous(), lse, scale)
+            do = _attn_operand(do, not use_v1 and _attn_strided(q, k))
+            dq, dk, dv = fn(q, k, v, do, lse, scale)
             return dq, dk, dv, None
         # General shapes: recompute P row-exactly from the saved log-sum-exp,
         # then the grads are plain batched GEMMs (library GEMM on MFMA).
@@ -784,8 +877,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
     if _use_hip(q):
         D = q.shape[-1]
         if D % 8 == 0 and D <= 128:
-            return _AttentionFn.apply(q.contiguous(), k.contiguous(),
-                                      v.contiguous(), scale)
+            strided = _attn_strided(q, k)
+            return _AttentionFn.apply(_attn_operand(q, strided),
+                                      _attn_operand(k, strided),
+                                      _attn_operand(v, strided), scale)
     return reference.attention(q, k, v, scale)
 
 
