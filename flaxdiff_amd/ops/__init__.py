@@ -131,33 +131,45 @@ def _grad_sink(p: Optional[torch.Tensor], kind: str) -> Optional[torch.Tensor]:
 # GroupNorm (+ optional fused SiLU)
 # ---------------------------------------------------------------------------
 
+def _gn_save(ctx, x, gamma, beta, mean, rstd, groups, silu):
+    ctx.save_for_backward(x, gamma, mean, rstd)
+    ctx.groups = groups
+    ctx.silu = silu
+    ctx.beta = beta
+    ctx.gamma_param = gamma
+
+
+def _gn_backward(ctx, dy, add):
+    """(dx, dgamma, dbeta) of gn_silu; `add` (or None) is summed into dx.
+    With live gradient sinks on both gamma and beta the kernel adds into
+    them and None comes back for both."""
+    x, gamma, mean, rstd = ctx.saved_tensors
+    ext = _require_ext()
+    has_beta = ctx.beta is not None
+    beta = ctx.beta if has_beta else torch.zeros_like(gamma)
+    if has_beta and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
+        sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
+        if sg is not None and sb is not None:
+            (dx,) = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta, mean,
+                                    rstd, ctx.groups, ctx.silu, sg, sb, add)
+            return dx, None, None
+    dx, dgamma, dbeta = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta, mean,
+                                        rstd, ctx.groups, ctx.silu,
+                                        None, None, add)
+    return dx, dgamma, (dbeta if has_beta else None)
+
+
 class _GroupNormSiLUFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, groups, eps, silu):
         ext = _require_ext()
         y, mean, rstd = ext.gn_silu_fwd(x, gamma, beta, groups, eps, silu)
-        ctx.save_for_backward(x, gamma, mean, rstd)
-        ctx.groups = groups
-        ctx.silu = silu
-        ctx.has_beta = beta is not None
-        ctx.beta = beta
-        ctx.gamma_param = gamma
+        _gn_save(ctx, x, gamma, beta, mean, rstd, groups, silu)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, gamma, mean, rstd = ctx.saved_tensors
-        ext = _require_ext()
-        beta = ctx.beta if ctx.has_beta else torch.zeros_like(gamma)
-        if ctx.has_beta and ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
-            if sg is not None and sb is not None:
-                (dx,) = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta, mean,
-                                        rstd, ctx.groups, ctx.silu, sg, sb)
-                return dx, None, None, None, None, None
-        dx, dgamma, dbeta = ext.gn_silu_bwd(dy.contiguous(), x, gamma, beta,
-                                            mean, rstd, ctx.groups, ctx.silu)
-        return dx, dgamma, (dbeta if ctx.has_beta else None), None, None, None
+        return (*_gn_backward(ctx, dy, None), None, None, None)
 
 
 def group_norm(x: torch.Tensor, groups: int, gamma: torch.Tensor,
@@ -180,35 +192,19 @@ class _GroupNormForkFn(torch.autograd.Function):
         # zero-filled tensor: an unused x_pass then costs nothing
         ctx.set_materialize_grads(False)
         y, mean, rstd = ext.gn_silu_fwd(x, gamma, beta, groups, eps, silu)
-        ctx.save_for_backward(x, gamma, mean, rstd)
-        ctx.groups = groups
-        ctx.silu = silu
-        ctx.beta = beta
-        ctx.gamma_param = gamma
+        _gn_save(ctx, x, gamma, beta, mean, rstd, groups, silu)
         return y, x                         # autograd re-wraps x as its own view
 
     @staticmethod
     def backward(ctx, dy, dx_pass):
-        x, gamma, mean, rstd = ctx.saved_tensors
-        ext = _require_ext()
         if dy is None:                      # only the pass-through was used
             return dx_pass, None, None, None, None, None
         add = None
         if dx_pass is not None:
             # a fresh dx is written; dx_pass is only read (it is usually a dy
             # that conv2's dgrad/wgrad read as well)
-            add = dx_pass.to(x.dtype).contiguous()
-        if ctx.needs_input_grad[1] and ctx.needs_input_grad[2]:
-            sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
-            if sg is not None and sb is not None:
-                (dx,) = ext.gn_silu_bwd(dy.contiguous(), x, gamma, ctx.beta,
-                                        mean, rstd, ctx.groups, ctx.silu,
-                                        sg, sb, add)
-                return dx, None, None, None, None, None
-        dx, dgamma, dbeta = ext.gn_silu_bwd(dy.contiguous(), x, gamma, ctx.beta,
-                                            mean, rstd, ctx.groups, ctx.silu,
-                                            None, None, add)
-        return dx, dgamma, dbeta, None, None, None
+            add = dx_pass.to(ctx.saved_tensors[0].dtype).contiguous()
+        return (*_gn_backward(ctx, dy, add), None, None, None)
 
 
 def group_norm_fork_enabled() -> bool:
@@ -262,43 +258,6 @@ def rms_norm(x: torch.Tensor, gamma: torch.Tensor, eps: float = 1e-5) -> torch.T
 # Conv2d NHWC (3x3 SAME / 1x1 / stride-2) — LDS-tiled implicit GEMM on MFMA
 # ---------------------------------------------------------------------------
 
-def _conv2d_wgrad_gemms(dy: torch.Tensor, x: torch.Tensor, kh: int, kw: int,
-                        stride: int) -> torch.Tensor:
-    """Weight gradient as KH*KW shifted-view GEMMs on MFMA (hipBLASLt).
-
-    dw[r,s,ci,co] = sum_m x[b, oh*st+r-pt, ow*st+s-pl, ci] * dy[b,oh,ow,co]
-    over the in-bounds output positions. Each (r,s) tap is one [Ci x M']@[M' x Co]
-    library GEMM over a strided view — no im2col materialization. A fully
-    hand-written LDS-tiled wgrad kernel is the planned replacement.
-    """
-    B, H, W, Ci = x.shape
-    _, OH, OW, Co = dy.shape
-    pt = max((OH - 1) * stride + kh - H, 0) // 2
-    pl = max((OW - 1) * stride + kw - W, 0) // 2
-    dw = torch.zeros(kh, kw, Ci, Co, dtype=torch.float32, device=x.device)
-    for r in range(kh):
-        oh_lo = max(0, -((pt - r) // -stride))  # ceil((pt-r)/stride), clamped
-        oh_hi = min(OH - 1, (H - 1 - r + pt) // stride)
-        if oh_hi < oh_lo:
-            continue
-        ih_lo = oh_lo * stride + r - pt
-        noh = oh_hi - oh_lo + 1
-        for s in range(kw):
-            ow_lo = max(0, -((pl - s) // -stride))
-            ow_hi = min(OW - 1, (W - 1 - s + pl) // stride)
-            if ow_hi < ow_lo:
-                continue
-            iw_lo = ow_lo * stride + s - pl
-            now = ow_hi - ow_lo + 1
-            x_sub = x[:, ih_lo:ih_lo + (noh - 1) * stride + 1:stride,
-                      iw_lo:iw_lo + (now - 1) * stride + 1:stride, :]
-            dy_sub = dy[:, oh_lo:oh_hi + 1, ow_lo:ow_hi + 1, :]
-            a = x_sub.reshape(-1, Ci)
-            b = dy_sub.reshape(-1, Co)
-            dw[r, s] += (a.transpose(0, 1) @ b).float()
-    return dw
-
-
 def _kernel_view(p: torch.Tensor) -> torch.Tensor:
     """bf16 tensor the compute kernels consume. An fp32 master param with a
     bf16 shadow (trainer/optim.py) uses the shadow — no cast kernel; the
@@ -331,6 +290,30 @@ def _routable_param(p: Optional[torch.Tensor]) -> bool:
         getattr(p, "_shadow_bf16", None) is not None
 
 
+def _save_params(ctx, w, b):
+    """Forward half of the parameter-gradient bookkeeping of the conv-like
+    Functions: the parameters (their gradient sinks hang off them) and dtypes."""
+    ctx.has_bias = b is not None
+    ctx.w_dtype = w.dtype
+    ctx.b_dtype = b.dtype if b is not None else None
+    ctx.w_param, ctx.b_param = w, b
+
+
+def _param_grads(ctx, ext, dy, x, kh, kw, stride):
+    """Backward half: (dw, db) for weight = input 1 and bias = input 2 of the
+    Function. `x` is the conv input [B,H,W,Ci] (only read when the weight
+    gradient is needed)."""
+    dw = db = None
+    b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
+        else None
+    if ctx.needs_input_grad[1]:
+        dw, db = _wgrad(ext, dy, x, kh, kw, stride,
+                        ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
+    elif ctx.has_bias:
+        db = _bias_grad(dy, b_param, ctx.b_dtype)
+    return dw, db
+
+
 class _Conv2dFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, stride, add, badd):
@@ -345,12 +328,9 @@ class _Conv2dFn(torch.autograd.Function):
                            badd if badd is not None else torch.Tensor())
         ctx.save_for_backward(x, wk)
         ctx.stride = stride
-        ctx.has_bias = b is not None
         ctx.has_add = add is not None
         ctx.has_badd = badd is not None
-        ctx.w_dtype = w.dtype
-        ctx.b_dtype = b.dtype if b is not None else None
-        ctx.w_param, ctx.b_param = w, b
+        _save_params(ctx, w, b)
         return y
 
     @staticmethod
@@ -360,14 +340,8 @@ class _Conv2dFn(torch.autograd.Function):
         dy = dy.contiguous()
         dx = ext.conv2d_dgrad(dy, wk, ctx.stride, x.shape[1], x.shape[2]) \
             if ctx.needs_input_grad[0] else None
-        dw = db = None
-        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
-            else None
-        if ctx.needs_input_grad[1]:
-            dw, db = _wgrad(ext, dy, x, wk.shape[0], wk.shape[1], ctx.stride,
-                            ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
-        elif ctx.has_bias:
-            db = _bias_grad(dy, b_param, ctx.b_dtype)
+        dw, db = _param_grads(ctx, ext, dy, x, wk.shape[0], wk.shape[1],
+                              ctx.stride)
         dadd = dy if ctx.has_add else None   # y = conv + add -> d(add) = dy
         dbadd = None
         if ctx.has_badd:                     # d(badd)[b,c] = sum_hw dy
@@ -403,11 +377,8 @@ class _DenseFn(torch.autograd.Function):
             if add is not None:
                 y = y + add
         ctx.save_for_backward(x2d, wk)
-        ctx.has_bias = b is not None
         ctx.has_add = add is not None
-        ctx.w_dtype = w2d.dtype
-        ctx.b_dtype = b.dtype if b is not None else None
-        ctx.w_param, ctx.b_param = w2d, b
+        _save_params(ctx, w2d, b)
         return y
 
     @staticmethod
@@ -422,18 +393,11 @@ class _DenseFn(torch.autograd.Function):
                 dx = torch.matmul(dy, wk.t())
         else:
             dx = None
-        dw = db = None
-        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
-            else None
-        if ctx.needs_input_grad[1]:
-            M = x2d.shape[0]
-            dw, db = _wgrad(ext, dy.view(M, 1, 1, dy.shape[1]),
-                            x2d.view(M, 1, 1, x2d.shape[1]), 1, 1, 1,
-                            ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
-            if dw is not None:
-                dw = dw.view(x2d.shape[1], dy.shape[1])
-        elif ctx.has_bias:
-            db = _bias_grad(dy, b_param, ctx.b_dtype)
+        M = x2d.shape[0]
+        dw, db = _param_grads(ctx, ext, dy.view(M, 1, 1, dy.shape[1]),
+                              x2d.view(M, 1, 1, x2d.shape[1]), 1, 1, 1)
+        if dw is not None:
+            dw = dw.view(x2d.shape[1], dy.shape[1])
         dadd = dy if ctx.has_add else None   # y = xW + add -> d(add) = dy
         return dx, dw, db, dadd
 
@@ -510,10 +474,7 @@ class _ConvUp2xFn(torch.autograd.Function):
         if y is None or y.numel() == 0:   # undefined tensor -> None via pybind
             raise _ConvUpIneligibleError
         ctx.save_for_backward(x, wk)
-        ctx.has_bias = b is not None
-        ctx.w_dtype = w.dtype
-        ctx.b_dtype = b.dtype if b is not None else None
-        ctx.w_param, ctx.b_param = w, b
+        _save_params(ctx, w, b)
         return y
 
     @staticmethod
@@ -522,18 +483,12 @@ class _ConvUp2xFn(torch.autograd.Function):
         ext = _require_ext()
         dy = dy.contiguous()
         H2, W2 = x.shape[1] * 2, x.shape[2] * 2
-        dx = db = dw = None
-        b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
-            else None
+        dx = None
         if ctx.needs_input_grad[0]:
             dx_up = ext.conv2d_dgrad(dy, wk, 1, H2, W2)
             dx = ext.upsample2x_bwd(dx_up)
-        if ctx.needs_input_grad[1]:
-            x_up = ext.upsample2x_fwd(x)
-            dw, db = _wgrad(ext, dy, x_up, 3, 3, 1, ctx.w_param, ctx.w_dtype,
-                            b_param, ctx.b_dtype)
-        elif ctx.has_bias:
-            db = _bias_grad(dy, b_param, ctx.b_dtype)
+        x_up = ext.upsample2x_fwd(x) if ctx.needs_input_grad[1] else None
+        dw, db = _param_grads(ctx, ext, dy, x_up, 3, 3, 1)
         return dx, dw, db
 
 
@@ -791,8 +746,9 @@ def depthwise_conv2d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
 
 
 # ---------------------------------------------------------------------------
-# Attention (softmax fp32) — hand-written flash kernel forward; backward
-# recomputes P from saved LSE and runs the 5 grads as MFMA GEMMs.
+# Attention (softmax fp32) — hand-written flash kernel forward; small-KV
+# shapes (Skv<=128, D<=64) take the fused flash backward kernel, the rest
+# recompute P from the saved LSE and compose the grads from batched GEMMs.
 # ---------------------------------------------------------------------------
 
 def _attn_view_ok(t: torch.Tensor) -> bool:
@@ -898,7 +854,6 @@ def forward_diffusion(x0, eps, signal_rate, noise_rate):
 
 def nearest_upsample_2x(x: torch.Tensor) -> torch.Tensor:
     if _use_hip(x):
-        ext = _require_ext()
         return _Upsample2xFn.apply(x.contiguous())
     return reference.nearest_upsample_2x_nhwc(x)
 
@@ -935,7 +890,7 @@ def fourier_time_embedding(t: torch.Tensor, freqs: torch.Tensor) -> torch.Tensor
 
 
 # ---------------------------------------------------------------------------
-# Fused Adam + EMA optimizer step (HIP kernel, one pass over params)
+# S5 diagonal scan; fused AdamW + EMA optimizer step
 # ---------------------------------------------------------------------------
 
 class _S5ScanFn(torch.autograd.Function):

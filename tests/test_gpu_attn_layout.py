@@ -9,6 +9,11 @@ forward outputs and dq are compared bit for bit with the call on
 are held to the fp32-autograd criterion of
 `test_attn_bwd_smallkv_matches_reference`.
 """
+import json
+import os
+import subprocess
+import sys
+
 import pytest
 import torch
 
@@ -270,3 +275,47 @@ def test_dense_operands_are_taken_as_before():
     _, dq_r, dk_r, dv_r = _autograd_reference(q, k, v, do, scale)
     for got, want in ((dq, dq_r), (dk, dk_r), (dv, dv_r)):
         assert _rel(got, want) < 0.05
+
+
+_FIRST_USE_CHILD = r"""
+import json, torch
+from flaxdiff_amd.ops import _require_ext
+ext = _require_ext()
+out = {}
+for B, H, Sq, Skv, D in ((1, 2, 64, 77, 64), (1, 2, 64, 77, 32)):
+    torch.manual_seed(0)
+    q, k, v, do = ((torch.randn(B, H, S, D, device="cuda") * 0.5).bfloat16()
+                   for S in (Sq, Skv, Skv, Sq))
+    scale = D ** -0.5
+    o, lse = ext.attn_fwd(q, k, v, scale)
+    got = ext.attn_bwd_smallkv_v2(q, k, v, do, lse, scale)
+    torch.cuda.synchronize()
+    qf, kf, vf = (t.float().requires_grad_(True) for t in (q, k, v))
+    s = torch.einsum("bhqd,bhkd->bhqk", qf, kf) * scale
+    ref = torch.einsum("bhqk,bhkd->bhqd", torch.softmax(s, dim=-1), vf)
+    ref.backward(do.float())
+    for name, g, want in zip(("dq", "dk", "dv"), got, (qf.grad, kf.grad, vf.grad)):
+        err = (g.float() - want).abs().max().item()
+        out[f"D{D}.{name}"] = err / (want.abs().max().item() + 1e-6)
+print("RESULT " + json.dumps(out))
+"""
+
+
+def test_backward_v2_first_use_in_fresh_process():
+    """The max-dynamic-LDS attribute is set once per process and per kernel
+    instantiation, on first launch. A fresh process runs <64,3> and then
+    <32,3> (same Skv tile count, different D panel): the second must get its
+    own attribute (it asks for ~152 KB of LDS). dq/dk/dv of both calls are
+    held to the fp32-autograd criterion of
+    `test_attn_bwd_smallkv_matches_reference`. Sq=64 keeps the D=64 call
+    clear of the LDS-size defect KERNELS.md documents for D>32."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", _FIRST_USE_CHILD], cwd=root,
+                       capture_output=True, text=True, timeout=180)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    line = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1]
+    errs = json.loads(line[len("RESULT "):])
+    print(errs)
+    assert len(errs) == 6
+    for name, rel in errs.items():
+        assert rel < 0.05, f"{name}: rel err {rel:.4f}"

@@ -578,14 +578,16 @@ def test_graph_captured_sampling_matches_eager():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("entry", ["attn_bwd_smallkv", "attn_bwd_smallkv_v2"])
 @pytest.mark.parametrize("B,H,Sq,Skv,D", [
     (2, 4, 64, 77, 16),    # level-0 cross-attn shape class
     (2, 4, 128, 77, 32),   # level-1
     (1, 4, 64, 64, 32),    # middle-block self-attn
     (3, 2, 100, 13, 16),   # ragged
 ])
-def test_attn_bwd_smallkv_matches_reference(B, H, Sq, Skv, D):
-    """Fused small-KV attention backward vs fp32 torch autograd."""
+def test_attn_bwd_smallkv_matches_reference(entry, B, H, Sq, Skv, D):
+    """Fused small-KV attention backward (v1 and v2 entry points) vs fp32
+    torch autograd."""
     torch.manual_seed(0)
     q = (torch.randn(B, H, Sq, D, device="cuda") * 0.5).to(torch.bfloat16)
     k = (torch.randn(B, H, Skv, D, device="cuda") * 0.5).to(torch.bfloat16)
@@ -597,7 +599,7 @@ def test_attn_bwd_smallkv_matches_reference(B, H, Sq, Skv, D):
     from flaxdiff_amd.ops import _require_ext
     ext = _require_ext()
     o, lse = ext.attn_fwd(q, k, v, scale)
-    dq, dk, dv = ext.attn_bwd_smallkv(q, k, v, do.contiguous(), lse, scale)
+    dq, dk, dv = getattr(ext, entry)(q, k, v, do.contiguous(), lse, scale)
 
     # fp32 autograd oracle
     qf, kf, vf = (t.float().requires_grad_(True) for t in (q, k, v))
