@@ -374,9 +374,33 @@ class ResidualBlock(nn.Module):
             return norm(x, silu=True)
         return self.activation(norm(x))
 
+    def _virtual_cat_ok(self, x, skip) -> bool:
+        rc = self.residual_conv
+        return isinstance(self.norm1, GroupNorm) and isinstance(rc, Conv) \
+            and rc.stride == 1 and ops.virtual_cat_eligible(
+                x, skip, self.norm1.num_groups, self.norm1.weight,
+                self.norm1.bias, rc.weight, rc.bias)
+
     def forward(self, x: torch.Tensor, temb: torch.Tensor,
-                textemb: torch.Tensor = None, extra_features: torch.Tensor = None):
-        if isinstance(self.norm1, GroupNorm):
+                textemb: torch.Tensor = None, extra_features: torch.Tensor = None,
+                skip: torch.Tensor = None):
+        """`skip`: the block's input is cat(x, skip) along channels. On the
+        HIP bf16 path norm1 and the 1x1 shortcut read the two tensors
+        directly (ops.group_norm_cat_dense); otherwise they are concatenated."""
+        residual_done = False
+        if skip is not None and not self._virtual_cat_ok(x, skip):
+            x = ops.cat_channels(x, skip)
+            skip = None
+        if skip is not None:
+            rc = self.residual_conv
+            out, residual = ops.group_norm_cat_dense(
+                x, skip, self.norm1.num_groups, self.norm1.weight,
+                self.norm1.bias, self.norm1.eps, self._fused_silu,
+                rc.weight, rc.bias)
+            residual_done = True
+            if not self._fused_silu:
+                out = self.activation(out)
+        elif isinstance(self.norm1, GroupNorm):
             # x feeds norm1 and the residual branch: the fork hands both
             # gradients to the GroupNorm backward kernel
             out, residual = self.norm1.forward_fork(x, silu=self._fused_silu)
@@ -394,7 +418,7 @@ class ResidualBlock(nn.Module):
             out = self.conv1(out) + t[:, None, None, :]
 
         out = self._norm_act(self.norm2, out)
-        if self.residual_conv is not None:
+        if self.residual_conv is not None and not residual_done:
             residual = self.residual_conv(residual)
         if isinstance(self.conv2, Conv) and residual.shape[-1] == self.features:
             # residual add fused into the conv epilogue (saves one full

@@ -181,16 +181,15 @@ class Unet(nn.Module):
 
         for level in self.up_blocks:
             for res, attn in zip(level["res"], level["attn"]):
-                x = ops.cat_channels(x, downs.pop())
-                x = res(x, temb)
+                # skip concat: virtual inside the block where it can be
+                x = res(x, temb, skip=downs.pop())
                 if not isinstance(attn, nn.Identity):
                     x = attn(x, textcontext)
             if "up" in level:
                 x = level["up"](x)
 
         x = self.conv_mid(x)
-        x = ops.cat_channels(x, downs.pop())
-        x = self.final_residual(x, temb)
+        x = self.final_residual(x, temb, skip=downs.pop())
 
         if isinstance(self.conv_out_norm, GroupNorm):
             x = self.conv_out_norm(x, silu=True)

@@ -299,16 +299,18 @@ def _save_params(ctx, w, b):
     ctx.w_param, ctx.b_param = w, b
 
 
-def _param_grads(ctx, ext, dy, x, kh, kw, stride):
+def _param_grads(ctx, ext, dy, x, kh, kw, stride, x_up2x=False):
     """Backward half: (dw, db) for weight = input 1 and bias = input 2 of the
     Function. `x` is the conv input [B,H,W,Ci] (only read when the weight
-    gradient is needed)."""
+    gradient is needed); with `x_up2x` it is the quarter-size source of a
+    nearest-2x upsample that feeds the conv."""
     dw = db = None
     b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[2] \
         else None
     if ctx.needs_input_grad[1]:
         dw, db = _wgrad(ext, dy, x, kh, kw, stride,
-                        ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype)
+                        ctx.w_param, ctx.w_dtype, b_param, ctx.b_dtype,
+                        x_up2x=x_up2x)
     elif ctx.has_bias:
         db = _bias_grad(dy, b_param, ctx.b_dtype)
     return dw, db
@@ -463,8 +465,10 @@ class _ConvUp2xFn(torch.autograd.Function):
     """nearest-2x upsample + 3x3 SAME conv as ONE kernel: the upsample is an
     address remap inside the conv's halo staging (no materialized big
     tensor on the forward; reference common.py:203-226 Upsample).
-    Backward rematerializes the upsampled activation once for wgrad and
-    folds the upsample adjoint (2x2 window sum) over the conv dgrad."""
+    Backward: wgrad reads x through the same (row>>1, pixel>>1) remap in
+    its slab staging (the extension materializes the upsampled activation
+    only for shapes that kernel declines, or under FD_WGRAD_UP_REMAP=0);
+    the upsample adjoint (2x2 window sum) runs over the conv dgrad."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -487,8 +491,7 @@ class _ConvUp2xFn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx_up = ext.conv2d_dgrad(dy, wk, 1, H2, W2)
             dx = ext.upsample2x_bwd(dx_up)
-        x_up = ext.upsample2x_fwd(x) if ctx.needs_input_grad[1] else None
-        dw, db = _param_grads(ctx, ext, dy, x_up, 3, 3, 1)
+        dw, db = _param_grads(ctx, ext, dy, x, 3, 3, 1, x_up2x=True)
         return dx, dw, db
 
 
@@ -558,8 +561,118 @@ def cat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return torch.cat([a, b], dim=-1)
 
 
+# ---------------------------------------------------------------------------
+# Virtual concat: GroupNorm(+SiLU) and the 1x1 shortcut of cat(a, b) without
+# the concatenated tensor (the UNet decoder's skip concat feeds exactly these
+# two consumers, both inside ResidualBlock)
+# ---------------------------------------------------------------------------
+
+def virtual_cat_enabled() -> bool:
+    """FD_VIRTUAL_CAT=0 restores the materialized skip concat."""
+    return os.environ.get("FD_VIRTUAL_CAT", "1") != "0"
+
+
+def virtual_cat_eligible(a: torch.Tensor, b: torch.Tensor, groups: int,
+                         gamma: torch.Tensor, beta: Optional[torch.Tensor],
+                         w: torch.Tensor, bias: Optional[torch.Tensor]) -> bool:
+    """Whether group_norm_cat_dense can take (a, b): HIP bf16, GroupNorm with
+    beta and the fork enabled, a 1x1 weight on the hand-GEMM route, Ca / Cb /
+    Cout multiples of 64 (a GEMM k-step and a wgrad ci tile then lie in one
+    source), channels per group a multiple of 8, C <= 2048."""
+    if not (virtual_cat_enabled() and group_norm_fork_enabled()
+            and _use_hip(a) and not _GEMM_LIB):
+        return False
+    if a.dtype != torch.bfloat16 or b.dtype != torch.bfloat16 \
+            or a.dim() != 4 or a.shape[:-1] != b.shape[:-1] or beta is None:
+        return False
+    ca, cb = a.shape[-1], b.shape[-1]
+    c = ca + cb
+    if w.dim() != 4 or w.shape[0] != 1 or w.shape[1] != 1 or w.shape[2] != c \
+            or not (_routable_param(w) and _routable_param(bias)):
+        return False
+    return ca % 64 == 0 and cb % 64 == 0 and w.shape[3] % 64 == 0 \
+        and groups > 0 and c % groups == 0 and (c // groups) % 8 == 0 \
+        and c <= 2048 and gamma.numel() == c
+
+
+class _GNCatDenseFn(torch.autograd.Function):
+    """(h, r) = (GroupNorm(+SiLU)(cat(a, b)), cat(a, b) @ w + bias) with the
+    concat only virtual: the GroupNorm kernels, the NT GEMM and the dense
+    wgrad read a and b as two sources. Backward: the shortcut's dx (gemm_dx of
+    dr, dense [M, Ca+Cb]) rides into the GroupNorm backward as its `add`, and
+    that kernel writes da and db directly — no concat, no split."""
+
+    @staticmethod
+    def forward(ctx, a, b, gamma, beta, groups, eps, silu, w, bias):
+        ext = _require_ext()
+        ctx.set_materialize_grads(False)    # an unused output arrives as None
+        ca, cb, n = a.shape[-1], b.shape[-1], w.shape[3]
+        h, mean, rstd = ext.gn_silu_fwd(a, gamma, beta, groups, eps, silu, b)
+        bf = bias if bias is not None else torch.Tensor()
+        if bf.numel() and bf.dtype != torch.float32:
+            bf = bf.float()
+        wt = getattr(w, "_shadow_bf16_t", None)
+        if wt is None:
+            wt = _kernel_view(w).reshape(ca + cb, n).t().contiguous()
+        r = ext.gemm_nt(a.view(-1, ca), wt, bf, torch.Tensor(), b.view(-1, cb))
+        ctx.save_for_backward(a, b, gamma, mean, rstd,
+                              _kernel_view(w).reshape(ca + cb, n))
+        ctx.groups, ctx.silu = groups, silu
+        ctx.beta, ctx.gamma_param = beta, gamma
+        _save_params(ctx, w, bias)
+        return h, r.view(*a.shape[:-1], n)
+
+    @staticmethod
+    def backward(ctx, dh, dr):
+        a, b, gamma, mean, rstd, wk = ctx.saved_tensors
+        ext = _require_ext()
+        ca, cb = a.shape[-1], b.shape[-1]
+        M = a.numel() // ca
+        add = dw = dbias = None
+        if dr is not None:
+            dr2 = dr.contiguous().view(M, -1)
+            if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+                add = ext.gemm_dx(dr2, wk).view(*a.shape[:-1], ca + cb)
+            b_param = ctx.b_param if ctx.has_bias and ctx.needs_input_grad[8] \
+                else None
+            if ctx.needs_input_grad[7]:
+                dw, dbias = _wgrad(ext, dr2.view(M, 1, 1, -1),
+                                   a.view(M, 1, 1, ca), 1, 1, 1,
+                                   ctx.w_param, ctx.w_dtype, b_param,
+                                   ctx.b_dtype if b_param is not None else None,
+                                   x2=b.view(M, 1, 1, cb))
+            elif b_param is not None:
+                dbias = _bias_grad(dr2, b_param, ctx.b_dtype)
+        if dh is None:                      # only the shortcut was used
+            da = db = None
+            if add is not None:
+                da, db = ext.split2_lastdim(add, ca, cb)
+            return da, db, None, None, None, None, None, dw, dbias
+        dh = dh.contiguous()
+        if ctx.needs_input_grad[2] and ctx.needs_input_grad[3]:
+            sg, sb = _grad_sink(ctx.gamma_param, "g"), _grad_sink(ctx.beta, "g")
+            if sg is not None and sb is not None:
+                da, db = ext.gn_silu_bwd(dh, a, gamma, ctx.beta, mean, rstd,
+                                         ctx.groups, ctx.silu, sg, sb, add, b)
+                return da, db, None, None, None, None, None, dw, dbias
+        da, db, dgamma, dbeta = ext.gn_silu_bwd(
+            dh, a, gamma, ctx.beta, mean, rstd, ctx.groups, ctx.silu,
+            None, None, add, b)
+        return da, db, dgamma, dbeta, None, None, None, dw, dbias
+
+
+def group_norm_cat_dense(a: torch.Tensor, b: torch.Tensor, groups: int,
+                         gamma: torch.Tensor, beta: torch.Tensor, eps: float,
+                         silu: bool, w: torch.Tensor,
+                         bias: Optional[torch.Tensor]):
+    """-> (group_norm(cat(a, b)), conv1x1(cat(a, b), w, bias)) without the
+    concatenated tensor. The caller checks `virtual_cat_eligible` first."""
+    return _GNCatDenseFn.apply(a.contiguous(), b.contiguous(), gamma, beta,
+                               groups, eps, silu, w, bias)
+
+
 def _wgrad(ext, dy, x, kh, kw, stride, w_param, w_dtype,
-           b_param=None, b_dtype=None):
+           b_param=None, b_dtype=None, x_up2x=False, x2=None):
     """(dw, db) through the split-M kernels; `b_dtype` set asks for the bias
     gradient too. With a live gradient sink on a parameter the reduce adds
     into it and None comes back for that gradient (autograd then has nothing
@@ -569,8 +682,11 @@ def _wgrad(ext, dy, x, kh, kw, stride, w_param, w_dtype,
     want_db = b_dtype is not None
     w_sink = _grad_sink(w_param, "w") if w_dtype == torch.float32 else None
     b_sink = _grad_sink(b_param, "b") if b_dtype == torch.float32 else None
+    # the trailing arguments only where they are set: the plain call keeps
+    # the signature every caller and stand-in of the extension knows
+    extra = (x_up2x, x2) if x2 is not None else (True,) if x_up2x else ()
     dw, db, folded = ext.conv2d_wgrad(dy, x, kh, kw, stride, w_sink,
-                                      want_db, b_sink)
+                                      want_db, b_sink, *extra)
     if dw is not None and w_dtype != torch.float32:
         dw = dw.to(w_dtype)
     if want_db and not folded:
