@@ -34,6 +34,8 @@ CASES = [
     (1, 4, 40, 77, 128),    # forward <1,4>, composed backward
     (1, 2, 200, 200, 32),   # forward only, several KV tiles
     (2, 3, 100, 13, 24),    # non-power-of-two H and D
+    (2, 2, 296, 77, 64),    # v2 <64,3>: three q iterations, all four waves
+    (2, 4, 296, 111, 32),   # v2 <32,4>: four waves, ragged last iteration
 ]
 BWD_V2_CASES = [c for c in CASES if c[3] <= 128 and c[4] <= 64]
 
@@ -282,7 +284,7 @@ import json, torch
 from flaxdiff_amd.ops import _require_ext
 ext = _require_ext()
 out = {}
-for B, H, Sq, Skv, D in ((1, 2, 64, 77, 64), (1, 2, 64, 77, 32)):
+for B, H, Sq, Skv, D in ((1, 2, 160, 77, 64), (1, 2, 64, 77, 32)):
     torch.manual_seed(0)
     q, k, v, do = ((torch.randn(B, H, S, D, device="cuda") * 0.5).bfloat16()
                    for S in (Sq, Skv, Skv, Sq))
@@ -307,8 +309,7 @@ def test_backward_v2_first_use_in_fresh_process():
     <32,3> (same Skv tile count, different D panel): the second must get its
     own attribute (it asks for ~152 KB of LDS). dq/dk/dv of both calls are
     held to the fp32-autograd criterion of
-    `test_attn_bwd_smallkv_matches_reference`. Sq=64 keeps the D=64 call
-    clear of the LDS-size defect KERNELS.md documents for D>32."""
+    `test_attn_bwd_smallkv_matches_reference`."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-c", _FIRST_USE_CHILD], cwd=root,
                        capture_output=True, text=True, timeout=180)

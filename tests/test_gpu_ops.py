@@ -424,7 +424,9 @@ def test_attn_spiked_softmax():
     assert rel_err(o.cpu(), ref) < 3e-2
 
 
-def test_attn_backward_composed():
+def test_attn_backward_fused_v2_route():
+    """Skv=77, D=32 through ops.attention: the fused v2 backward (the composed
+    route is held to a reference in test_gpu_attention_grid.py)."""
     torch.manual_seed(7)
     B, H, Sq, Skv, D = 1, 2, 64, 77, 32
     q_cpu = torch.randn(B, H, Sq, D)
@@ -577,15 +579,21 @@ def test_graph_captured_sampling_matches_eager():
     assert (eager - graphed).abs().max() < 2e-2
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("entry", ["attn_bwd_smallkv", "attn_bwd_smallkv_v2"])
-@pytest.mark.parametrize("B,H,Sq,Skv,D", [
+_ATTN_BWD_SMALLKV_CASES = [(B, H, Sq, Skv, D, entry) for B, H, Sq, Skv, D in [
     (2, 4, 64, 77, 16),    # level-0 cross-attn shape class
     (2, 4, 128, 77, 32),   # level-1
     (1, 4, 64, 64, 32),    # middle-block self-attn
     (3, 2, 100, 13, 16),   # ragged
-])
-def test_attn_bwd_smallkv_matches_reference(entry, B, H, Sq, Skv, D):
+] for entry in ("attn_bwd_smallkv", "attn_bwd_smallkv_v2")] + [
+    # level-2 cross-attn: D=64 (v2 only), all four waves hold valid rows
+    (1, 2, 256, 77, 64, "attn_bwd_smallkv_v2"),
+]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,H,Sq,Skv,D,entry", _ATTN_BWD_SMALLKV_CASES,
+                         ids=["-".join(map(str, c)) for c in _ATTN_BWD_SMALLKV_CASES])
+def test_attn_bwd_smallkv_matches_reference(B, H, Sq, Skv, D, entry):
     """Fused small-KV attention backward (v1 and v2 entry points) vs fp32
     torch autograd."""
     torch.manual_seed(0)
