@@ -863,8 +863,9 @@ def depthwise_conv2d(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
 
 # ---------------------------------------------------------------------------
 # Attention (softmax fp32) — hand-written flash kernel forward; small-KV
-# shapes (Skv<=128, D<=64) take the fused flash backward kernel, the rest
-# recompute P from the saved LSE and compose the grads from batched GEMMs.
+# shapes (Skv<=128, D<=64) take the fused flash backward kernel, the rest the
+# key-streaming flash backward. FD_ATTN_BWD_STREAM=0 recomputes P from the
+# saved LSE and composes the grads from batched GEMMs instead.
 # ---------------------------------------------------------------------------
 
 def _attn_view_ok(t: torch.Tensor) -> bool:
@@ -881,18 +882,40 @@ def _attn_view_ok(t: torch.Tensor) -> bool:
     return all(st > 0 and st % 8 == 0 for st in t.stride()[:3])
 
 
+def attn_stream_geometry(D: int):
+    """(DP, KB, QS) of `attn_bwd_stream` at head dim D: padded head width,
+    keys per workgroup, rows per query slice. Mirrors the table in
+    hip/attention_bwd_stream.hip (the extension reports its own through
+    `attn_bwd_stream_geometry`; a GPU test holds the two together)."""
+    dp = 32 if D <= 32 else 64 if D <= 64 else 128
+    return dp, (128 if dp <= 64 else 64), 32
+
+
+def _attn_bwd_route(Sq: int, Skv: int, D: int) -> str:
+    """Which backward an `_AttentionFn` of this shape runs: "v1" / "v2" (the
+    small-KV kernels, Skv <= 128 and D <= 32 / 64), "stream" (the
+    key-streaming kernel: everything else), or "composed" (fp32 batched
+    GEMMs, only with FD_ATTN_BWD_STREAM=0)."""
+    use_v1 = os.environ.get("FD_ATTN_BWD_V1")
+    if Skv <= 128 and D <= (32 if use_v1 else 64):
+        return "v1" if use_v1 else "v2"
+    if os.environ.get("FD_ATTN_BWD_STREAM", "1") == "0":
+        return "composed"
+    return "stream"
+
+
 def _attn_strided(q: torch.Tensor, k: torch.Tensor) -> bool:
     """Strided route: q/k/v/do go to the kernels as the views they are and
     o/dq/dk/dv come back in the layouts of q/q/k/v, so the model's
-    reshape+permute on either side of attention costs no copy kernel. Only
-    where the backward is the v2 small-KV kernel; the v1 route and the
-    composed backward keep their contiguous copies. FD_ATTN_STRIDED=0
-    restores the copies everywhere."""
+    reshape+permute on either side of attention costs no copy kernel. Where
+    the backward is the v2 small-KV kernel or the streaming kernel; the v1
+    route and the composed backward (FD_ATTN_BWD_STREAM=0) keep their
+    contiguous copies. FD_ATTN_STRIDED=0 restores the copies everywhere."""
     if os.environ.get("FD_ATTN_STRIDED", "1") == "0":
         return False
     if os.environ.get("FD_ATTN_BWD_V1"):
         return False
-    return k.shape[2] <= 128 and q.shape[3] <= 64
+    return _attn_bwd_route(q.shape[2], k.shape[2], q.shape[3]) in ("v2", "stream")
 
 
 def _attn_operand(t: torch.Tensor, strided: bool) -> torch.Tensor:
@@ -904,27 +927,35 @@ class _AttentionFn(torch.autograd.Function):
     def forward(ctx, q, k, v, scale):
         ext = _require_ext()
         o, lse = ext.attn_fwd(q, k, v, scale)
-        ctx.save_for_backward(q, k, v, lse)
+        # o feeds the streaming backward's delta = rowsum(dO * O)
+        ctx.save_for_backward(q, k, v, o, lse)
         ctx.scale = scale
         return o
 
     @staticmethod
     def backward(ctx, do):
-        q, k, v, lse = ctx.saved_tensors
+        q, k, v, o, lse = ctx.saved_tensors
         scale = ctx.scale
         # Small-KV fused MFMA flash backward: 3x the composed GEMM path at
         # the bench shapes (2.34 vs 7.12 ms at Sq=4096 D=16 — tools/
-        # attn_bwd_ab.py). Larger head dims fall through to the GEMMs.
-        use_v1 = os.environ.get("FD_ATTN_BWD_V1")
-        dmax = 32 if use_v1 else 64
-        if k.shape[2] <= 128 and q.shape[3] <= dmax:
+        # attn_bwd_ab.py). Every other shape streams over key blocks
+        # (attention_bwd_stream.hip): no [Sq,Skv] tensor, no library GEMM.
+        route = _attn_bwd_route(q.shape[2], k.shape[2], q.shape[3])
+        if route in ("v1", "v2"):
             ext = _require_ext()
+            use_v1 = route == "v1"
             fn = ext.attn_bwd_smallkv if use_v1 else ext.attn_bwd_smallkv_v2
             do = _attn_operand(do, not use_v1 and _attn_strided(q, k))
             dq, dk, dv = fn(q, k, v, do, lse, scale)
             return dq, dk, dv, None
-        # General shapes: recompute P row-exactly from the saved log-sum-exp,
-        # then the grads are plain batched GEMMs (library GEMM on MFMA).
+        if route == "stream":
+            ext = _require_ext()
+            do = _attn_operand(do, _attn_strided(q, k))
+            dq, dk, dv = ext.attn_bwd_stream(q, k, v, o, do, lse, scale)
+            return dq, dk, dv, None
+        # FD_ATTN_BWD_STREAM=0: recompute P row-exactly from the saved
+        # log-sum-exp, then the grads are plain batched GEMMs (library GEMM
+        # on MFMA) over fp32 [B,H,Sq,Skv] tensors.
         qf, kf, vf, dof = q.float(), k.float(), v.float(), do.float()
         s = torch.einsum("bhqd,bhkd->bhqk", qf, kf) * scale
         p = torch.exp(s - lse.unsqueeze(-1))
