@@ -213,6 +213,20 @@ def test_gemm_nt_split_x(Ka, Kb, N):
     2 * 24 * 24,     # 18 row tiles: the split-X kernel itself
 ])
 def test_dense_wgrad_split_x(M, Ca, Cb, Co, sinks):
+    _dense_wgrad_split_x(M, Ca, Cb, Co, sinks)
+
+
+@pytest.mark.parametrize("sinks", [False, True])
+def test_dense_wgrad_split_x_multitile(sinks):
+    """The split-X kernel's steady state: 5 tiles per block through its ring
+    of 4 buffers (1 in the last block), both sources in use."""
+    M, Ca, Cb, Co = 4224, 256, 256, 512
+    plan = _require_ext().wgrad_tr16_plan(M, 1, 1, Ca + Cb, Co, 1)
+    assert tuple(plan) == ("dense", 14, 5)        # 66 tiles = 13 * 5 + 1
+    _dense_wgrad_split_x(M, Ca, Cb, Co, sinks)
+
+
+def _dense_wgrad_split_x(M, Ca, Cb, Co, sinks):
     ext = _require_ext()
     a, b, dy, cat = _split_inputs(M, Ca, Cb, Co)
     Ci = Ca + Cb

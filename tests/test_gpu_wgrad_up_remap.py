@@ -81,8 +81,14 @@ def _check(got, want, spread, what):
     ((2, 16, 16, 64), 128),   # output W = 32: 2 rows per tile
     ((1, 32, 32, 64), 64),    # output W = 64: 1 row per tile, chunked reduce
     ((2, 4, 4, 64), 64),      # output W = 8: the remap declines, x is rebuilt
+    # output W = 32, 5 tiles per block (2 in the last): slabs re-staged through
+    # the remap as the ring wraps
+    ((7, 16, 16, 256), 320),
 ])
 def test_wgrad_up_remap(xshape, Co, sinks):
+    if xshape == (7, 16, 16, 256):
+        plan = _require_ext().wgrad_tr16_plan(7, 32, 32, 256, Co, 3)
+        assert tuple(plan) == ("v3", 23, 5)       # 112 tiles = 22 * 5 + 2
     c = _case(xshape, Co, sinks)
     x_before = c["x"].clone()
     got_w, got_b = _route(c["dy"], c["x"], True, sinks)

@@ -219,21 +219,64 @@ def _channel_means(co):
     return (torch.arange(co, dtype=torch.float32) - co / 2 + 0.5) / co
 
 
-# (id, B, HW, Ci, Co, k, stride, exact, bound, folds the bias gradient)
+# (id, B, H, W, Ci, Co, k, stride, exact, bound, folds the bias gradient, plan)
+# plan: None, or the geometry the case was written for, asserted through
+# `wgrad_tr16_plan`: (family, Z, tiles per block, tiles of the last block).
+# The *_multitile / *_ringwrap cases run the kernels' steady state: several
+# tiles per block (ring slots and dY buffers reused, the look-ahead clamped at
+# the tail), a last block with fewer tiles than the others, and Z <= 32 so the
+# reduce order is fixed.
 _CONV_CASES = [
-    ("v3_w16", 2, 16, 64, 64, 3, 1, True, 4e-2, True),
-    ("v3_w16_nci2", 2, 16, 128, 64, 3, 1, True, 4e-2, True),  # only ci0==0 tile
-    ("v3_w16_nco2", 2, 16, 64, 128, 3, 1, True, 4e-2, True),
-    ("v3_w32", 2, 32, 64, 64, 3, 1, True, 4e-2, True),
-    ("v3_w64_atomic", 1, 64, 64, 64, 3, 1, False, 4e-2, True),   # Z=64
-    ("w8", 4, 8, 128, 64, 3, 1, True, 4e-2, True),
-    ("generic_stride2", 2, 16, 64, 64, 3, 2, True, 5e-2, False),
+    ("v3_w16", 2, 16, 16, 64, 64, 3, 1, True, 4e-2, True, None),
+    ("v3_w16_nci2", 2, 16, 16, 128, 64, 3, 1, True, 4e-2, True, None),  # only ci0==0 tile
+    ("v3_w16_nco2", 2, 16, 16, 64, 128, 3, 1, True, 4e-2, True, None),
+    ("v3_w32", 2, 32, 32, 64, 64, 3, 1, True, 4e-2, True, None),
+    ("v3_w64_atomic", 1, 64, 64, 64, 64, 3, 1, False, 4e-2, True, None),   # Z=64
+    ("w8", 4, 8, 8, 128, 64, 3, 1, True, 4e-2, True, None),
+    ("generic_stride2", 2, 16, 16, 64, 64, 3, 2, True, 5e-2, False, None),
+    ("v3_w64_multitile", 1, 64, 64, 256, 320, 3, 1, True, 4e-2, True,
+     ("v3", 22, 3, 1)),
+    ("v3_w32_multitile", 7, 32, 32, 256, 320, 3, 1, True, 4e-2, True,
+     ("v3", 23, 5, 2)),
+    # 20 image rows per block through a ring of 14 slabs
+    ("v3_w16_ringwrap", 26, 16, 16, 256, 320, 3, 1, True, 4e-2, True,
+     ("v3", 21, 5, 4)),
+    ("v3_w128_multitile", 1, 70, 128, 256, 256, 3, 1, True, 4e-2, True,
+     ("v3", 24, 3, 1)),
+    ("w8_multitile", 70, 8, 8, 256, 256, 3, 1, True, 4e-2, True,
+     ("w8", 24, 3, 1)),
 ]
-# (id, M, Ci, Co, exact)
+# (id, M, Ci, Co, exact, plan)
 _DENSE_CASES = [
-    ("dense_nzc1", 256, 64, 128, True),
-    ("dense_z40_atomic", 64 * 40, 128, 64, False),
+    ("dense_nzc1", 256, 64, 128, True, None),
+    ("dense_z40_atomic", 64 * 40, 128, 64, False, None),
+    # 5 tiles per block through a ring of 4 buffers
+    ("dense_multitile", 4224, 512, 512, True, ("dense", 14, 5, 1)),
 ]
+
+
+def _check_plan(plan, B, H, W, Ci, Co, k):
+    """The case reaches the kernel geometry it was written for."""
+    family, Z, tpb, last = plan
+    assert tuple(_ext().wgrad_tr16_plan(B, H, W, Ci, Co, k)) == (family, Z, tpb)
+    ntiles = {"dense": B * H * W // 64, "w8": B,
+              "v3": B * H // {16: 4, 32: 2, 64: 1, 128: 1}.get(W, 1)}[family]
+    assert tpb > 1 and ntiles - (Z - 1) * tpb == last and 0 < last < tpb
+    assert Z <= 32                                # one z-chunk: fixed order
+
+
+def _wgrad_ref_3x3_same(x, dy):
+    """fp64 dw of a stride-1 3x3 SAME conv as nine [Ci, M] @ [M, Co] matmuls
+    (the same sums as the conv backward, at matmul speed on the CPU)."""
+    B, H, W, Ci = x.shape
+    Co = dy.shape[-1]
+    xp = torch.nn.functional.pad(x.double(), (0, 0, 1, 1, 1, 1))
+    d2 = dy.double().reshape(-1, Co)
+    dw = torch.empty(3, 3, Ci, Co, dtype=torch.float64)
+    for r in range(3):
+        for s in range(3):
+            dw[r, s] = xp[:, r:r + H, s:s + W].reshape(-1, Ci).t() @ d2
+    return dw
 
 
 def _check_wgrad(x, dy, k, stride, ref, exact, bound, folds=None):
@@ -308,24 +351,31 @@ def _check_bias(x, dy, k, stride, dw_plain, exact, bound, folds):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("B,HW,Ci,Co,k,stride,exact,bound,folds",
+@pytest.mark.parametrize("B,H,W,Ci,Co,k,stride,exact,bound,folds,plan",
                          [c[1:] for c in _CONV_CASES],
                          ids=[c[0] for c in _CONV_CASES])
-def test_conv_wgrad_sink(B, HW, Ci, Co, k, stride, exact, bound, folds):
+def test_conv_wgrad_sink(B, H, W, Ci, Co, k, stride, exact, bound, folds, plan):
     torch.manual_seed(0)
-    x = (torch.randn(B, HW, HW, Ci) * 0.5).bfloat16()
-    OH = HW // stride
-    dy = (torch.randn(B, OH, OH, Co) * 0.5 + _channel_means(Co)).bfloat16()
-    w = torch.zeros(k, k, Ci, Co, dtype=torch.float64, requires_grad=True)
-    reference.conv2d_nhwc(x.double(), w, None, stride=stride,
-                          padding="same").backward(dy.double())
-    _check_wgrad(x.cuda(), dy.cuda(), k, stride, w.grad, exact, bound, folds)
+    x = (torch.randn(B, H, W, Ci) * 0.5).bfloat16()
+    dy = (torch.randn(B, H // stride, W // stride, Co) * 0.5
+          + _channel_means(Co)).bfloat16()
+    if plan is not None:
+        _check_plan(plan, B, H, W, Ci, Co, k)
+        ref = _wgrad_ref_3x3_same(x, dy)
+    else:
+        w = torch.zeros(k, k, Ci, Co, dtype=torch.float64, requires_grad=True)
+        reference.conv2d_nhwc(x.double(), w, None, stride=stride,
+                              padding="same").backward(dy.double())
+        ref = w.grad
+    _check_wgrad(x.cuda(), dy.cuda(), k, stride, ref, exact, bound, folds)
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("M,Ci,Co,exact", [c[1:] for c in _DENSE_CASES],
+@pytest.mark.parametrize("M,Ci,Co,exact,plan", [c[1:] for c in _DENSE_CASES],
                          ids=[c[0] for c in _DENSE_CASES])
-def test_dense_wgrad_sink(M, Ci, Co, exact):
+def test_dense_wgrad_sink(M, Ci, Co, exact, plan):
+    if plan is not None:
+        _check_plan(plan, M, 1, 1, Ci, Co, 1)
     torch.manual_seed(1)
     x = (torch.randn(M, Ci) * 0.5).bfloat16()
     dy = (torch.randn(M, Co) * 0.5 + _channel_means(Co)).bfloat16()
