@@ -40,7 +40,8 @@ FAST_SHAPES = [
 # two m-tiles per block (more than 768 m-tiles): the epilogue runs mid-loop
 # with bias held across tiles
 MULTI_TILE = (256 * 769 + 40, 64, 64)
-GENERIC_SHAPES = [(384, 64, 96), (256, 64, 40)]
+# N = 38 is no multiple of 4: a 4-column store then a 2-column tail per lane
+GENERIC_SHAPES = [(384, 64, 96), (256, 64, 40), (256, 64, 38)]
 VARIANTS = ["none", "bias", "add", "bias_add", "x2"]
 
 _CASES = {}

@@ -163,7 +163,9 @@ def test_conv2d_fwd(B, H, W, Ci, Co, k, st):
     (2, 16, 16, 64, 128),        # general igemm path
     (2, 8, 8, 512, 512),         # halo path (v2-eligible)
     (2, 64, 64, 64, 64),         # level-0 halo v1 path
-    (2, 48, 48, 32, 32),         # general kernel, Co not mult of 4 tails
+    (2, 48, 48, 32, 32),         # general kernel (W does not tile); Co = 32
+                                 # has no column tails: those are in
+                                 # test_gpu_conv_generic_tier.py
 ])
 def test_conv2d_fused_residual_add(B, H, W, Ci, Co):
     """conv2d(add=residual) == conv2d() + residual, fwd and the dadd=dy

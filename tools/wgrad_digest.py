@@ -6,9 +6,13 @@ fixed and its output bytes are a function of the code alone: run this on two
 builds and compare the lines. Cases: the exact cases of
 tests/test_grad_sinks.py, tests/test_gpu_wgrad_up_remap.py and
 tests/test_gpu_virtual_cat.py, including the multi-tile ones.
+The generic_* cases are those of tests/test_gpu_conv_generic_tier.py that
+have Z <= 32: the split-M `conv2d_wgrad_kernel` with channel tails.
 Prints one line per case: name, sha256(dw)[:16], sha256(db)[:16].
+`--integer` draws x and dy from {-1, 0, 1} instead of random bf16.
 """
 import hashlib
+import sys
 
 import torch
 
@@ -29,6 +33,11 @@ CONV = [
     ("w8_multitile", 70, 8, 8, 256, 256, 3, 1),
     ("dense_nzc1", 256, 1, 1, 64, 128, 1, 1),
     ("dense_multitile", 4224, 1, 1, 512, 512, 1, 1),
+    ("generic_db_tails", 5, 5, 16, 20, 6, 3, 1),
+    ("generic_db_w24", 2, 12, 24, 20, 6, 3, 1),
+    ("generic_stride2_tails", 3, 15, 15, 20, 70, 3, 2),
+    ("generic_1x1_stride2", 2, 8, 8, 20, 6, 1, 2),
+    ("generic_dense_tails", 200, 1, 1, 20, 6, 1, 1),
 ]
 # (name, x shape [B, h, w, Ci], Co): dy is [B, 2h, 2w, Co]
 UP = [
@@ -50,8 +59,14 @@ def digest(t):
         .hexdigest()[:16]
 
 
+INTEGER = "--integer" in sys.argv[1:]
+
+
 def inputs(seed, xshape, dyshape):
     gen = torch.Generator().manual_seed(seed)
+    if INTEGER:
+        return tuple(torch.randint(-1, 2, s, generator=gen).bfloat16().cuda()
+                     for s in (xshape, dyshape))
     x = (torch.randn(*xshape, generator=gen) * 0.5).bfloat16().cuda()
     dy = (torch.randn(*dyshape, generator=gen) * 0.5 + 0.125).bfloat16().cuda()
     return x, dy
@@ -60,7 +75,7 @@ def inputs(seed, xshape, dyshape):
 def main():
     ext = _require_ext()
     for name, B, H, W, Ci, Co, k, st in CONV:
-        x, dy = inputs(11, (B, H, W, Ci), (B, H // st, W // st, Co))
+        x, dy = inputs(11, (B, H, W, Ci), (B, -(-H // st), -(-W // st), Co))
         dw, db, _ = ext.conv2d_wgrad(dy, x, k, k, st, None, True, None)
         print(name, digest(dw), digest(db))
     for name, xs, Co in UP:
